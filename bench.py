@@ -5,6 +5,13 @@ A "step" is one enf_flow_apply over the whole N-sample batch (one fused launch):
 Y (D x N) and ladj (N) are written once, inputs already resident in HBM.
 
     python bench.py [--gpus N --steps K --warmup W] [--D 32 --N 10000000 --pairs 4 --dtype f32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set-up, the settle and warmup launches, the K timed
+steps, the output dump when --dump-outputs is given, and the one JSON line. Everything else the benchmark
+measures (the cache-resident "warm" leg of a small working set, the copy ceiling, the in-run rocprofv3 passes
+or the committed PMC summary, the CPU baseline, the config-5 `train` object with the reference's examples)
+runs only with --full; their fields of the line are null without it.
 
 Multi-GPU: one process per GPU. Under torch.distributed.run (WORLD_SIZE set) each process is one
 rank; `python bench.py --gpus N` started by hand starts the N ranks itself (enf_launch.py: child
@@ -375,6 +382,15 @@ def main():
                          "its steady clock: the first ~25 launches of the 0.7 ms headline kernel run 0.86 -> 0.63 ms "
                          "(profiles/r04_bench_order_*.json), longer than the driver's 5 warmup steps; 200 ms leaves a 10x margin "
                          "for nodes whose power management settles more slowly; 0 disables")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the warm (cache-resident) leg of --cache auto, "
+                         "the copy ceiling, the rocprofv3 PMC / kernel-stats passes (or the committed summary), the "
+                         "CPU baseline and the config-5 training leg (--no-cpu / --no-train / --no-pmc drop one of "
+                         "them again); off: set-up, settle, warmup, the timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/Y.npy (D x M) and "
+                         "DIR/ladj.npy (M) in the run's dtype: all N columns, or a fixed seeded sample of M of them "
+                         "(in ascending order) when N columns would exceed 32 MB; several ranks: Y_rank<r>.npy, ...")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-train", action="store_true", help="skip the config-5 training leg (`train` object)")
     ap.add_argument("--train-timeout", type=float, default=240.0,
@@ -401,6 +417,8 @@ def main():
                     help="CPU tests only: the launch / barrier / max-over-ranks harness on gloo with a CPU "
                          "stand-in step (measures nothing)")
     args = ap.parse_args()
+    if args.dump_outputs and args.selftest_cpu:
+        ap.error("--dump-outputs needs the GPU path (--selftest-cpu computes nothing)")
 
     # N > 1 started by hand: start the N ranks as child processes before anything touches a GPU
     rc = enf_launch.spawn_ranks_if_needed(args.gpus, os.path.abspath(__file__), sys.argv[1:])
@@ -588,7 +606,7 @@ def main():
     mode = args.cache
     big = args.selftest_cpu or set_bytes >= (1 << 30)
     if mode == "auto":
-        mode = "warm" if big else "both"
+        mode = "warm" if big else ("both" if args.full else "cold")  # (the warm leg is not the headline's)
     cache, warm = None, None
     nsets = 1 if args.selftest_cpu else max(1, min(64, -(-(1 << 30) // set_bytes) + 1))
     if mode in ("cold", "both") and nsets > 1:
@@ -616,6 +634,8 @@ def main():
         cache = {"mode": "warm" if not big else "cold by size", "sets": 1, "set_MB": set_bytes / 1e6,
                  "why": ("one buffer set larger than 1 GiB: the 256 MiB Infinity Cache holds a fraction of it"
                          if big else "one buffer set read back to back: cache-resident, not an HBM figure")}
+    if args.dump_outputs:  # before any later leg touches the buffers (the copy ceiling overwrites Y)
+        dump_outputs(args.dump_outputs, sets[(cur["i"] - 1) % cur["k"]], D, world, rank)
     t_local, kern_ms_max = max_over_ranks([wall, kern_ms], dev, world)
     per_rank_kernel_ms = gather_ranks(kern_ms, dev, world, rank)
     ms_per_step = t_local / args.steps * 1e3
@@ -625,7 +645,7 @@ def main():
     bytes_per_launch = bytes_per_launch_of(N, D, esz)
     achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
     traffic, valu, rocprof = None, None, None
-    if not args.selftest_cpu:
+    if args.full and not args.selftest_cpu:
         live = None
         if world == 1 and not args.no_pmc and args.pattern is None and D in (32, 64, 128):
             try:
@@ -636,10 +656,10 @@ def main():
             traffic, valu, rocprof = live
         elif not args.inverse:
             traffic, valu = pmc_evidence(D, N, args)
-    copy = None if args.selftest_cpu else copy_ceiling(lib, X, Y, stream)
+    copy = copy_ceiling(lib, X, Y, stream) if args.full and not args.selftest_cpu else None
     copy_gbs = copy["GBps"] if copy else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.selftest_cpu and not args.inverse:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not args.selftest_cpu and not args.inverse:
         cpu = cpu_baseline(layers, D, np_dtype, args.cpu_seconds)
     headline = (D, N, args.pairs, args.dtype, args.pattern, args.inverse, strong) == (32, 10_000_000, 4, "f32", None,
                                                                                      False, False)
@@ -693,7 +713,9 @@ def main():
         }
     # the config-5 leg after the headline is measured; on several ranks under a watchdog, so that a collective that
     # never completes (libenf's own RCCL communicator) still leaves the headline line, with the train object's error
-    if args.selftest_cpu and not args.no_train:  # the config-5 leg's rank plumbing on gloo
+    if not args.full:
+        train = None
+    elif args.selftest_cpu and not args.no_train:  # the config-5 leg's rank plumbing on gloo
         import bench_train
 
         train = bench_train.train_leg_selftest(world, rank, steps=min(args.steps, 20))
@@ -721,6 +743,37 @@ def main():
         print(json.dumps(out), file=json_out, flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: Y and ladj together stay under this (a sample of the columns beyond it)
+
+
+def dump_columns(N, D, esz):
+    """The columns --dump-outputs writes: all N when Y and ladj fit DUMP_BYTES, else a sample of
+    DUMP_BYTES / ((D + 1) x esz) distinct columns drawn with a fixed seed, ascending (the same for every run
+    of the same N, D and dtype); None means all."""
+    m = DUMP_BYTES // ((D + 1) * esz)
+    if N <= m:
+        return None
+    return np.sort(np.random.default_rng(0xD0D0).choice(N, size=m, replace=False))
+
+
+def dump_outputs(dirname, bufs, D, world, rank):
+    """Write the Y and ladj of the buffer set `bufs` (the last timed step's) as DIR/Y.npy (D x M, the caller's
+    column-major view) and DIR/ladj.npy (M), in the run's dtype (float32 or float64)."""
+    import torch
+
+    _, Ys, Ls = bufs
+    N = Ys.shape[0]
+    cols = dump_columns(N, D, Ys.element_size())
+    torch.cuda.synchronize()
+    if cols is not None:
+        idx = torch.from_numpy(cols).to(Ys.device)
+        Ys, Ls = Ys.index_select(0, idx), Ls.index_select(0, idx)
+    os.makedirs(dirname, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(dirname, f"Y{tag}.npy"), Ys.cpu().numpy().T)
+    np.save(os.path.join(dirname, f"ladj{tag}.npy"), Ls.cpu().numpy())
 
 
 def train_leg(dev, world, rank):

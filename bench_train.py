@@ -158,7 +158,7 @@ def train_leg(dev, world, rank, D=32, N=10_000_000, nbatches=100, pairs=4, steps
               comm_kind="enf", history="", emulate_world=None, breakdown=False, dp_fused=True):
     """Config 5 on this process's GPU as one rank of `world` (torch.distributed initialised by the
     caller when world > 1): returns the result record (the same on every rank; rank 0 prints it).
-    Also run by bench.py after its headline measurement (`train` object of its JSON line).
+    Also run by bench.py --full after its headline measurement (`train` object of its JSON line).
     emulate_world=W (one process only): the data-parallel step of rank 0 of W ranks -- its share B/W of each
     minibatch, the gradient, a single-rank EnfComm all-reduce and enf_whitening_apply normalised by the whole
     minibatch B -- i.e. one rank's step at that world size without the cross-GPU transfer (the update differs

@@ -33,10 +33,63 @@ def test_bench_single_rank_line():
     assert out["settle"]["launches"] == 0 and "steady clock" in out["settle"]["why"]
     assert out["distributed"]["world_size"] == 1 and len(out["distributed"]["per_rank_kernel_ms"]) == 1
     assert out["value"] == pytest.approx(1000 * 3 / (out["ms_per_step"] * 3 / 1e3), rel=1e-6)
+    # a plain run (no --full) measures the headline only: no leg beside it
+    assert out["train"] is None and out["cpu_baseline"] is None and out["warm"] is None
+    assert out["roofline"]["copy_ceiling"] is None and out["valu"] is None
+
+
+def test_bench_dump_columns_are_fixed_and_bounded():
+    """--dump-outputs: all columns while Y and ladj fit the dump's byte bound, else a sample of distinct columns,
+    ascending, identical from call to call, whose Y and ladj stay within the bound (far under 64 MB)."""
+    import numpy as np
+
+    import bench
+
+    assert bench.dump_columns(1000, 32, 4) is None
+    assert bench.DUMP_BYTES <= 64 * 10**6
+    for D, esz in ((32, 4), (32, 8), (2, 8)):
+        a, b = bench.dump_columns(10_000_000, D, esz), bench.dump_columns(10_000_000, D, esz)
+        assert np.array_equal(a, b) and np.all(np.diff(a) > 0) and 0 <= a[0] and a[-1] < 10_000_000
+        assert a.size * (D + 1) * esz <= bench.DUMP_BYTES < (a.size + 1) * (D + 1) * esz
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_match_oracle(gpu, oracle, tmp_path):
+    """A plain run with --dump-outputs on the GPU: --steps sets the timed steps, the line carries ms_per_step and
+    no leg beside the headline, and DIR/Y.npy (D x N) / DIR/ladj.npy (N) hold what the timed path computed (the
+    oracle on the same seeded inputs, tests/parity.py's fp32 criterion); a second run writes the same values.
+    N = 4099: several blocks and a column tail; a set this small is timed over the rotating buffer sets as one
+    graph replay, so the dump reads the set of the last captured launch."""
+    import numpy as np
+    import torch
+
+    import bench
+    import parity
+
+    D, N = 32, 4099
+    outs = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup",
+                            "1", "--N", str(N), "--settle-ms", "0", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=240, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+        assert line["value"] == pytest.approx(N * 3 / (line["ms_per_step"] * 3 / 1e3), rel=1e-6)
+        assert line["train"] is None and line["cpu_baseline"] is None and line["roofline"]["copy_ceiling"] is None
+        assert sorted(os.listdir(tmp_path / d)) == ["Y.npy", "ladj.npy"]
+        outs.append((np.load(tmp_path / d / "Y.npy"), np.load(tmp_path / d / "ladj.npy")))
+    (Y, L), (Y2, L2) = outs
+    assert Y.dtype == np.float32 and L.dtype == np.float32 and Y.shape == (D, N) and L.shape == (N,)
+    assert np.array_equal(Y, Y2) and np.array_equal(L, L2)
+    g = torch.Generator(device=gpu).manual_seed(0x5EED)
+    X = torch.randn((N, D), generator=g, device=gpu, dtype=torch.float32).cpu().numpy().T
+    parity.check_vs_oracle(oracle, bench.build_flow(D, 4, np.float32), np.asfortranarray(X), Y, L, np.float32,
+                           what="bench --dump-outputs")
 
 
 def test_bench_launches_two_ranks():
-    out = run_bench("--gpus", "2")
+    out = run_bench("--gpus", "2", "--full")  # (--full: the config-5 leg beside the headline)
     assert out["n_gpus"] == 2
     d = out["distributed"]
     assert d["world_size"] == 2 and d["backend"] == "gloo" and d["data_path_collective"] is None
