@@ -60,16 +60,9 @@ enf_status device_info(enf::DeviceInfo* out) {
   return ENF_OK;
 }
 
+// parameter pointers of a layer (a HouseholderTrafo's columns are one array), or -1 for an unknown op
 int nparams_of(int op) {
-  switch (op) {
-    case ENF_OP_SCALESHIFT: return 2;
-    case ENF_OP_CENTER_STRETCH:
-    case ENF_OP_CENTER_CONTRACT: return 3;
-    case ENF_OP_JOHNSON:
-    case ENF_OP_JOHNSON_INV: return 4;
-    case ENF_OP_HOUSEHOLDER: return 1;
-    default: return -1;
-  }
+  return op < ENF_OP_SCALESHIFT || op > ENF_OP_HOUSEHOLDER ? -1 : enf::layer_param_vectors(op, 1);
 }
 
 enf_status validate_layers(int64_t D, const enf_layer* layers, int32_t nlayers) {
@@ -525,7 +518,7 @@ enf_status enf_flow_param_count(int64_t D, const enf_layer* layers, int32_t nlay
   if (vs != ENF_OK) return vs;
   int64_t n = 0;
   for (int32_t l = 0; l < nlayers; ++l)
-    n += D * (layers[l].op == ENF_OP_HOUSEHOLDER ? layers[l].k : nparams_of(layers[l].op));
+    n += D * enf::layer_param_vectors(layers[l].op, layers[l].k);
   *count = n;
   return ENF_OK;
   ENF_CATCH

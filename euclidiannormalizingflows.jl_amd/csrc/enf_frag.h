@@ -1,7 +1,7 @@
 // enf_frag.h -- device building blocks shared by the fused flow kernels (enf_flow.hip: step-table
-// interpreter; enf_flow_hj.hip: compiled (Householder o Johnson)^n program): hardware math, DPP group
-// sums, the 16-byte fragment layout of a column-major D x N batch, tile loads/stores and the
-// software-pipelined persistent tile loop.
+// interpreter; enf_flow_hj.hip: compiled (Householder o Johnson)^n program): hardware math, the
+// 16-byte fragment layout of a column-major D x N batch, tile loads/stores and the software-pipelined
+// persistent tile loop. The DPP group sums are enf_xlane.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "enf_internal.h"
+#include "enf_xlane.h"
 
 namespace enf {
 
@@ -44,52 +45,6 @@ __device__ __forceinline__ void log2_8_inplace(float (&x)[8]) {
   asm("v_log_f32 %0, %0\nv_log_f32 %1, %1\nv_log_f32 %2, %2\nv_log_f32 %3, %3\nv_log_f32 %4, %4\n"
       "v_log_f32 %5, %5\nv_log_f32 %6, %6\nv_log_f32 %7, %7\ns_nop 0"
       : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
-}
-
-// DPP cross-lane sum over aligned groups of G lanes (G <= 64, power of two). All 64 lanes must
-// be active. quad_perm(1,0,3,2) = 0xB1, quad_perm(2,3,0,1) = 0x4E, row_half_mirror = 0x141,
-// row_mirror = 0x140: after the quad steps every lane of a quad holds the quad sum, so a
-// mirror partner always lies in the other quad / half-row.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL,
-                                                               0xF, 0xF, false));
-}
-// (mov_dpp with bound_ctrl: every lane of these patterns reads a lane of its own row, so no `old` value is
-// needed and none is materialised -- update_dpp(0, ...) cost two v_mov of zero per stage; round 4)
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double x) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const int lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-  return __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
-template <int CTRL, typename T>
-__device__ __forceinline__ T dpp(T x) {
-  if constexpr (std::is_same_v<T, float>) return dpp_f<CTRL>(x);
-  else return dpp_d<CTRL>(x);
-}
-template <int G, typename T>
-__device__ __forceinline__ T group_sum(T x) {
-  if constexpr (G >= 2) x += dpp<0xB1>(x);
-  if constexpr (G >= 4) x += dpp<0x4E>(x);
-  if constexpr (G >= 8) x += dpp<0x141>(x);
-  if constexpr (G >= 16) x += dpp<0x140>(x);
-  if constexpr (G >= 32) x += __shfl_xor(x, 16);
-  if constexpr (G >= 64) x += __shfl_xor(x, 32);
-  return x;
-}
-
-// DPP max over aligned groups of G lanes (as group_sum)
-template <int G>
-__device__ __forceinline__ float group_max(float x) {
-  if constexpr (G >= 2) x = fmaxf(x, dpp<0xB1>(x));
-  if constexpr (G >= 4) x = fmaxf(x, dpp<0x4E>(x));
-  if constexpr (G >= 8) x = fmaxf(x, dpp<0x141>(x));
-  if constexpr (G >= 16) x = fmaxf(x, dpp<0x140>(x));
-  if constexpr (G >= 32) x = fmaxf(x, __shfl_xor(x, 16));
-  if constexpr (G >= 64) x = fmaxf(x, __shfl_xor(x, 32));
-  return x;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -33,8 +33,8 @@
 #include <initializer_list>
 #include <string>
 #include <type_traits>
-#include <vector>
 
+#include "enf_grad_chunked.h"
 #include "enf_grad_hj.h"
 #include "enf_grad_tail.h"
 #include "enf_internal.h"
@@ -92,62 +92,17 @@ __host__ __device__ constexpr int grad_lane_values(int D) {
   return D > 64 * (16 / (int)sizeof(T)) ? D / 64 : 16 / (int)sizeof(T);
 }
 
-__host__ __device__ constexpr int grad_nparams(int op) {
-  return op == OP_HOUSEHOLDER ? 1 : op == OP_SCALESHIFT ? 2 : (op == OP_JOHNSON || op == OP_JOHNSON_INV) ? 4 : 3;
-}
-
-typedef unsigned int u32x4g __attribute__((ext_vector_type(4)));
-
-template <int CTRL, typename T>
-__device__ __forceinline__ T gdpp(T x) {
-  if constexpr (std::is_same_v<T, float>) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false));
-  } else {
-    const uint64_t u = __builtin_bit_cast(uint64_t, x);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, false);
-    return __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-  }
-}
-template <int G, typename T>
-__device__ __forceinline__ T gsum(T x) {
-  if constexpr (G >= 2) x += gdpp<0xB1>(x);
-  if constexpr (G >= 4) x += gdpp<0x4E>(x);
-  if constexpr (G >= 8) x += gdpp<0x141>(x);
-  if constexpr (G >= 16) x += gdpp<0x140>(x);
-  if constexpr (G >= 32) x = add_xor_swap<16>(x);
-  if constexpr (G >= 64) x = add_xor_swap<32>(x);
-  return x;
-}
+// parameter vectors of one step (a Householder step is one column)
+__host__ __device__ constexpr int grad_nparams(int op) { return layer_param_vectors(op, 1); }
 
 // Add a per-lane contribution to the wave's double accumulator of row `row`: the lanes holding the
-// same row (all column slots of the wave) are summed with cross-lane shuffles first, then one lane
-// per row does a plain (non-atomic) read-modify-write -- every address has exactly one writer.
-// D >= V (CPF == 1): lanes with equal lane % G share rows; D < V: every lane holds all D rows.
-// Round 5: the stages within a 16-lane row are DPP moves (quad_perm xor 1 / xor 2, row_ror 4 / 8 -- shifts by a
-// multiple of the class size keep lanes in their class), only the two cross-row stages are ds_bpermute; a
-// bpermute round trip is several times a DPP move's latency and the examples' one-block steps are chains of these.
-template <int CTRL, typename T>
-__device__ __forceinline__ T wdpp(T x) {
-  if constexpr (std::is_same_v<T, float>) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-  } else {
-    const uint64_t u = __builtin_bit_cast(uint64_t, x);
-    const int lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-    return __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-  }
-}
-template <int G, int CPF, int SEG, typename T>
+// same row (all column slots of the wave: the lanes with equal lane % G; at D < V every lane holds all D rows) are
+// summed across the wave first (class_sum: DPP moves and permlane swaps -- a ds_bpermute round trip is several
+// times a DPP move's latency and the examples' one-block steps are chains of these; round 5), then one lane per
+// row does a plain (non-atomic) read-modify-write -- every address has exactly one writer.
+template <int G, typename T>
 __device__ __forceinline__ void wave_accumulate(double* __restrict__ acc, int row, T v, int lane, int nrows) {
-  (void)CPF;
-  (void)SEG;
-  if constexpr (G < 2) v += wdpp<0xB1>(v);   // quad_perm(1,0,3,2): lane ^ 1
-  if constexpr (G < 4) v += wdpp<0x4E>(v);   // quad_perm(2,3,0,1): lane ^ 2
-  if constexpr (G < 8) v += wdpp<0x124>(v);  // row_ror:4
-  if constexpr (G < 16) v += wdpp<0x128>(v); // row_ror:8
-  if constexpr (G < 32) v = add_xor_swap<16>(v);
-  if constexpr (G < 64) v = add_xor_swap<32>(v);
+  v = class_sum<G>(v);
   if (lane < G && row < nrows) acc[row] += (double)v;  // padded rows (row >= D) have no parameter
 }
 
@@ -173,8 +128,7 @@ template <typename T, int D>
 __host__ __device__ constexpr bool grad_fast_rows() { return std::is_same_v<T, double> && D <= kFastMaxD; }
 // record values per row of a step: the parameters, then (fast rows) the constants
 __host__ __device__ constexpr int rec_nparams(int op, bool fast) {
-  return (op == OP_HOUSEHOLDER ? 1 : op == OP_SCALESHIFT ? 2 : (op == OP_JOHNSON || op == OP_JOHNSON_INV) ? 4 : 3) +
-         (fast ? rec_extra(op) : 0);
+  return grad_nparams(op) + (fast ? rec_extra(op) : 0);
 }
 
 // the row constants of a step, from its parameters just written to the record r (value q of the row at r[q V]).
@@ -509,7 +463,7 @@ __device__ __forceinline__ bool bwd_fast_step(const double (&xin)[V], const doub
 #pragma unroll
   for (int q = 0; q < np; ++q)
 #pragma unroll
-    for (int k = 0; k < SEG; ++k) wave_accumulate<G, CPF, SEG>(gacc + q * Dr, r0 + k, dsum[q][k], lane, Dr);
+    for (int k = 0; k < SEG; ++k) wave_accumulate<G>(gacc + q * Dr, r0 + k, dsum[q][k], lane, Dr);
   return true;
 }
 
@@ -783,7 +737,7 @@ __device__ __forceinline__ void negll_grad_impl(const GradArgs& a, const ReduceA
           T dot = 0;
 #pragma unroll
           for (int e = 0; e < SEG; ++e) dot = fma(r[c * SEG + e], x[c * SEG + e], dot);
-          dot = gsum<G>(dot);
+          dot = group_sum<G, true>(dot);
 #pragma unroll
           for (int e = 0; e < SEG; ++e) x[c * SEG + e] = fma(-dot, r[c * SEG + e], x[c * SEG + e]);
         }
@@ -834,7 +788,7 @@ __device__ __forceinline__ void negll_grad_impl(const GradArgs& a, const ReduceA
         if (valid[e] && r0 + e % SEG < a.D) part += (x[e] * x[e] + (T)1.8378770664093454836) / (T)2;
 #pragma unroll
       for (int c = 0; c < CPF; ++c) {
-        const T tot = gsum<G>(lad[c]);  // all lanes active (DPP)
+        const T tot = group_sum<G, true>(lad[c]);  // all lanes active (DPP)
         if (valid[c * SEG] && (lane % G) == 0) part -= tot;
       }
       lossp += (double)part;
@@ -877,12 +831,12 @@ __device__ __forceinline__ void negll_grad_impl(const GradArgs& a, const ReduceA
             vx = fma(r[c * SEG + e], xin[c * SEG + e], vx);
             vg = fma(r[c * SEG + e], g[c * SEG + e], vg);
           }
-          vx = gsum<G>(vx);
-          vg = gsum<G>(vg);
+          vx = group_sum<G, true>(vx);
+          vg = group_sum<G, true>(vg);
 #pragma unroll
           for (int e = 0; e < SEG; ++e) {
             const T contrib = valid[c * SEG + e] ? g[c * SEG + e] * vx + xin[c * SEG + e] * vg : (T)0;
-            wave_accumulate<G, CPF, SEG>(gacc + a.goff[s], r0 + e, contrib, lane, a.D);
+            wave_accumulate<G>(gacc + a.goff[s], r0 + e, contrib, lane, a.D);
             g[c * SEG + e] = fma(-vg, r[c * SEG + e], g[c * SEG + e]);
           }
         }
@@ -927,7 +881,7 @@ __device__ __forceinline__ void negll_grad_impl(const GradArgs& a, const ReduceA
             const T clw = (ss1 && row != 0) ? (T)0 : (VJP ? cl[e / SEG] : (T)-1);
             const T gx = bwd_elem<T>(op, xin[e], g[e], p, dp, clw);
             for (int q = 0; q < np; ++q)
-              wave_accumulate<G, CPF, SEG>(gacc + a.goff[s] + q * a.D, row, valid[e] ? dp[q] : (T)0, lane, a.D);
+              wave_accumulate<G>(gacc + a.goff[s] + q * a.D, row, valid[e] ? dp[q] : (T)0, lane, a.D);
             g[e] = valid[e] ? gx : (T)0;
           }
         }
@@ -1060,7 +1014,7 @@ static_assert(sizeof(GradArgs) + sizeof(ReduceArgs) + sizeof(StepArgs) + 2 * siz
               "kernel arguments over 4 KB");
 
 // The update half of a data-parallel step (enf_whitening_apply): the same loss / ADAGrad /
-// re-normalisation as whitening_tail_kernel, reading the cross-rank sum g (1 + nparams values of T,
+// re-normalisation as grad_reduce_kernel's MODE_STEP, reading the cross-rank sum g (1 + nparams values of T,
 // the all-reduced enf_flow_negll_grad output) instead of the totals. Same operations and roundings
 // as out[0:1] / B + enf_adagrad_step per run + enf_householder_normalize_strided per batch.
 template <typename T>
@@ -1106,20 +1060,13 @@ bool grad_D_supported(int64_t D, bool f64) {
 }
 constexpr size_t kGradLdsMax = 160 * 1024;
 
-// kernel rows: D rounded up to a power of two
-int64_t grad_Dp(int64_t D) {
-  int64_t p = 1;
-  while (p < D) p <<= 1;
-  return p;
-}
-
 enf_status make_plan(bool f64, int64_t D, int64_t N, const enf_layer* layers, int32_t nlayers, Plan& P) {
   std::memset(&P.ga, 0, sizeof P.ga);
   std::memset(&P.ra, 0, sizeof P.ra);
   if (!grad_D_supported(D, f64))
     return set_error(ENF_ERR_UNSUPPORTED, "enf_flow_negll_grad: D must be <= 1024");
   if (nlayers > kMaxGradLayers) return set_error(ENF_ERR_UNSUPPORTED, "enf_flow_negll_grad: more than 16 layers");
-  const int64_t Dp = grad_Dp(D);
+  const int64_t Dp = next_pow2(D);  // kernel rows
   // one row per lane for fp64 D = 2 batches that then still fit one block (<= kSmallMaxWaves tiles of 32 columns)
   P.vl = (f64 && Dp == 2 && N <= 32 * kSmallMaxWaves) ? 1 : 0;
   const int V = P.vl ? P.vl : f64 ? grad_lane_values<double>((int)Dp) : grad_lane_values<float>((int)Dp);
@@ -1146,7 +1093,7 @@ enf_status make_plan(bool f64, int64_t D, int64_t N, const enf_layer* layers, in
       roff += rec_nparams(layers[l].op, fast) * nent;
       ++s;
     }
-    goff += (int)D * (layers[l].op == OP_HOUSEHOLDER ? layers[l].k : grad_nparams(layers[l].op));
+    goff += (int)D * layer_param_vectors(layers[l].op, layers[l].k);
   }
   P.ga.D = (int32_t)D;
   P.ga.Dp = (int32_t)Dp;
@@ -1271,104 +1218,75 @@ hipError_t launch_grad_D(const Plan& P, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <typename T, int DD, int VL = 0, class Prog = ProgInterp>
-hipError_t launch_step_small_D(const Plan& P, const StepArgs& sa, hipStream_t st) {
+// The one-block kernels: whitening_step_small_kernel (no trailing arguments) or whitening_epoch_small_kernel
+// (tail = N, bs), at the plan's rows per lane and compiled program.
+template <typename T, int DD, int VL = 0, class Prog = ProgInterp, typename... Tail>
+hipError_t launch_small_D(const Plan& P, const StepArgs& sa, hipStream_t st, Tail... tail) {
   if constexpr (VL == 0 && Prog::n == 0 && DD == 2 && std::is_same_v<T, double>) {
     if (P.vl == 1) {
-      if (P.prog == 2) return launch_step_small_D<T, DD, 1, ProgExample2d>(P, sa, st);
-      return launch_step_small_D<T, DD, 1>(P, sa, st);
+      if (P.prog == 2) return launch_small_D<T, DD, 1, ProgExample2d>(P, sa, st, tail...);
+      return launch_small_D<T, DD, 1>(P, sa, st, tail...);
     }
   }
   if constexpr (VL == 0 && Prog::n == 0 && DD == 1 && std::is_same_v<T, double>) {
-    if (P.prog == 1) return launch_step_small_D<T, DD, 0, ProgExample1d>(P, sa, st);
+    if (P.prog == 1) return launch_small_D<T, DD, 0, ProgExample1d>(P, sa, st, tail...);
   }
+  void (*kernel)(GradArgs, ReduceArgs, StepArgs, Tail...);
+  if constexpr (sizeof...(Tail) == 0) kernel = whitening_step_small_kernel<T, DD, VL, Prog>;
+  else kernel = whitening_epoch_small_kernel<T, DD, VL, Prog>;
   if (P.small_lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)whitening_step_small_kernel<T, DD, VL, Prog>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.small_lds);
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.small_lds);
     if (e != hipSuccess) return e;
   }
+  const GradArgs* ga = &P.ga;
 #if ENF_DIAG
   static const int ts = ENF_KNOB("ENF_SMALL_TS", 0);
+  GradArgs ga_ts;
   if (ts) {
-    GradArgs ga = P.ga;
-    ga.diag_ts = 1;
-    hipLaunchKernelGGL((whitening_step_small_kernel<T, DD, VL, Prog>), dim3(1), dim3(64 * P.nw), P.small_lds, st, ga, P.ra,
-                       sa);
-    return hipGetLastError();
+    ga_ts = P.ga;
+    ga_ts.diag_ts = 1;
+    ga = &ga_ts;
   }
 #endif
-  hipLaunchKernelGGL((whitening_step_small_kernel<T, DD, VL, Prog>), dim3(1), dim3(64 * P.nw), P.small_lds, st, P.ga, P.ra,
-                     sa);
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(64 * P.nw), P.small_lds, st, *ga, P.ra, sa, tail...);
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_step_small(const Plan& P, const StepArgs& sa, hipStream_t st) {
+// f(std::integral_constant<int, Dp>) at the plan's kernel rows Dp
+template <class F>
+hipError_t dispatch_Dp(const Plan& P, F&& f) {
   switch (P.ga.Dp) {
-#define ENF_S(DD) case DD: return launch_step_small_D<T, DD>(P, sa, st);
-    ENF_S(1) ENF_S(2) ENF_S(4) ENF_S(8) ENF_S(16) ENF_S(32) ENF_S(64) ENF_S(128) ENF_S(256) ENF_S(512) ENF_S(1024)
-#undef ENF_S
+#define ENF_DP(DD) case DD: return f(std::integral_constant<int, DD>());
+    ENF_DP(1) ENF_DP(2) ENF_DP(4) ENF_DP(8) ENF_DP(16) ENF_DP(32) ENF_DP(64) ENF_DP(128) ENF_DP(256) ENF_DP(512) ENF_DP(1024)
+#undef ENF_DP
     default: return hipErrorInvalidValue;
   }
 }
 
-template <typename T, int DD, int VL = 0, class Prog = ProgInterp>
-hipError_t launch_epoch_small_D(const Plan& P, const StepArgs& sa, int64_t N, int64_t bs, hipStream_t st) {
-  if constexpr (VL == 0 && Prog::n == 0 && DD == 2 && std::is_same_v<T, double>) {
-    if (P.vl == 1) {
-      if (P.prog == 2) return launch_epoch_small_D<T, DD, 1, ProgExample2d>(P, sa, N, bs, st);
-      return launch_epoch_small_D<T, DD, 1>(P, sa, N, bs, st);
-    }
-  }
-  if constexpr (VL == 0 && Prog::n == 0 && DD == 1 && std::is_same_v<T, double>) {
-    if (P.prog == 1) return launch_epoch_small_D<T, DD, 0, ProgExample1d>(P, sa, N, bs, st);
-  }
-  if (P.small_lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)whitening_epoch_small_kernel<T, DD, VL, Prog>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.small_lds);
-    if (e != hipSuccess) return e;
-  }
-#if ENF_DIAG
-  static const int ts = ENF_KNOB("ENF_SMALL_TS", 0);
-  if (ts) {
-    GradArgs ga = P.ga;
-    ga.diag_ts = 1;
-    hipLaunchKernelGGL((whitening_epoch_small_kernel<T, DD, VL, Prog>), dim3(1), dim3(64 * P.nw), P.small_lds, st, ga,
-                       P.ra, sa, N, bs);
-    return hipGetLastError();
-  }
-#endif
-  hipLaunchKernelGGL((whitening_epoch_small_kernel<T, DD, VL, Prog>), dim3(1), dim3(64 * P.nw), P.small_lds, st, P.ga, P.ra,
-                     sa, N, bs);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_epoch_small(const Plan& P, const StepArgs& sa, int64_t N, int64_t bs, hipStream_t st) {
-  switch (P.ga.Dp) {
-#define ENF_E(DD) case DD: return launch_epoch_small_D<T, DD>(P, sa, N, bs, st);
-    ENF_E(1) ENF_E(2) ENF_E(4) ENF_E(8) ENF_E(16) ENF_E(32) ENF_E(64) ENF_E(128) ENF_E(256) ENF_E(512) ENF_E(1024)
-#undef ENF_E
-    default: return hipErrorInvalidValue;
-  }
+template <typename T, typename... Tail>
+hipError_t launch_small(const Plan& P, const StepArgs& sa, hipStream_t st, Tail... tail) {
+  return dispatch_Dp(P, [&](auto dd) { return launch_small_D<T, decltype(dd)::value>(P, sa, st, tail...); });
 }
 
 template <typename T, bool VJP = false>
 hipError_t launch_grad(const Plan& P, hipStream_t st) {
-  hipError_t e0 = hipSuccess;
-  switch (P.ga.Dp) {
-#define ENF_G(DD) case DD: e0 = launch_grad_D<T, DD, VJP>(P, st); break;
-    ENF_G(1) ENF_G(2) ENF_G(4) ENF_G(8) ENF_G(16) ENF_G(32) ENF_G(64) ENF_G(128) ENF_G(256) ENF_G(512)
-    ENF_G(1024)
-#undef ENF_G
-    default: return hipErrorInvalidValue;
-  }
-  return e0;
+  return dispatch_Dp(P, [&](auto dd) { return launch_grad_D<T, decltype(dd)::value, VJP>(P, st); });
+}
+
+// the zeroed StepArgs of a reduction that updates nothing (MODE_OUT, MODE_SUM)
+StepArgs no_step() {
+  StepArgs none;
+  std::memset(&none, 0, sizeof none);
+  return none;
 }
 
 }  // namespace
 
-namespace {
+bool fits_one_launch(bool f64, int64_t D, int64_t N, const enf_layer* layers, int32_t nlayers) {
+  Plan P;
+  return make_plan(f64, D, N > 0 ? N : 1, layers, nlayers, P) == ENF_OK && P.lds <= kGradLdsMax;
+}
+
 enf_status single_workspace(bool f64, int64_t D, int64_t N, const enf_layer* layers, int32_t nlayers, size_t* bytes) {
   Plan P;
   enf_status s = make_plan(f64, D, N > 0 ? N : 1, layers, nlayers, P);
@@ -1376,6 +1294,8 @@ enf_status single_workspace(bool f64, int64_t D, int64_t N, const enf_layer* lay
   *bytes = plan_workspace_bytes(P);
   return ENF_OK;
 }
+
+namespace {
 
 // The per-block partial rows (fused (J o H)^n kernel or the generic one) in the workspace; P.ra then describes
 // them for grad_reduce_kernel (rows, the constant ladj the fused kernel computes once).
@@ -1402,8 +1322,7 @@ enf_status grad_parts(bool f64, int64_t D, int64_t N, const void* X, int64_t ldx
     P.ra.nblocks = P.blocks;
     P.ra.ctot = nullptr;
   }
-  if (e != hipSuccess) return set_error(ENF_ERR_HIP, hipGetErrorString(e));
-  return ENF_OK;
+  return hip_status(e);
 }
 
 }  // namespace
@@ -1414,10 +1333,7 @@ enf_status negll_grad_single(bool f64, int64_t D, int64_t N, const void* X, int6
   enf_status s = grad_parts(f64, D, N, X, ldx, layers, nlayers, workspace, workspace_bytes, st, P);
   if (s != ENF_OK) return s;
   P.ra.out = out;
-  StepArgs none;
-  std::memset(&none, 0, sizeof none);
-  hipError_t e = launch_reduce<MODE_OUT>(f64, P.ra, none, st);
-  return e == hipSuccess ? ENF_OK : set_error(ENF_ERR_HIP, hipGetErrorString(e));
+  return hip_status(launch_reduce<MODE_OUT>(f64, P.ra, no_step(), st));
 }
 
 enf_status flow_vjp_single(bool f64, int64_t D, int64_t N, const void* X, int64_t ldx, const void* dY, int64_t lddy,
@@ -1445,55 +1361,21 @@ enf_status flow_vjp_single(bool f64, int64_t D, int64_t N, const void* X, int64_
     P.ra.ctot = nullptr;
     P.ra.out = dparams;
     P.ra.skip_loss = 1;
-    StepArgs none;
-    std::memset(&none, 0, sizeof none);
-    e = launch_reduce<MODE_OUT>(f64, P.ra, none, st);
+    e = launch_reduce<MODE_OUT>(f64, P.ra, no_step(), st);
   }
-  if (e != hipSuccess) return set_error(ENF_ERR_HIP, hipGetErrorString(e));
-  return ENF_OK;
-}
-
-enf_status whitening_apply(bool f64, int64_t D, int64_t nparams, const void* g, int64_t B, void* theta, void* acc,
-                           const int64_t* runs, int32_t nruns, const int64_t* hb, int32_t nhb, double eta,
-                           double epsilon, double* loss_out, hipStream_t st) {
-  if (nruns < 0 || nruns > kMaxStepRuns || nhb < 0 || nhb > kMaxStepHB)
-    return set_error(ENF_ERR_UNSUPPORTED, "enf_whitening_apply: too many parameter runs or Householder batches");
-  StepArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.theta = theta;
-  a.acc = acc;
-  a.loss_out = loss_out;
-  a.scale = 1.0 / (double)B;
-  a.eta = eta;
-  a.eps = epsilon;
-  a.D = D;
-  a.nsamp = B;
-  a.nruns = nruns;
-  a.nhb = nhb;
-  for (int i = 0; i < nruns; ++i) {
-    a.runs[i][0] = runs[2 * i];
-    a.runs[i][1] = runs[2 * i + 1];
-    if (a.runs[i][0] < 0 || a.runs[i][1] < a.runs[i][0] || a.runs[i][1] > nparams)
-      return set_error(ENF_ERR_INVALID, "enf_whitening_apply: parameter run outside theta");
-  }
-  for (int i = 0; i < nhb; ++i) {
-    for (int q = 0; q < 3; ++q) a.hb[i][q] = hb[3 * i + q];
-    if (a.hb[i][0] < 0 || a.hb[i][1] < 0 || a.hb[i][2] < D ||
-        (a.hb[i][1] > 0 && a.hb[i][0] + (a.hb[i][1] - 1) * a.hb[i][2] + D > nparams))
-      return set_error(ENF_ERR_INVALID, "enf_whitening_apply: Householder batch outside theta");
-  }
-  if (f64) hipLaunchKernelGGL((whitening_apply_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)g, a);
-  else hipLaunchKernelGGL((whitening_apply_kernel<float>), dim3(1), dim3(256), 0, st, (const float*)g, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ENF_OK : set_error(ENF_ERR_HIP, hipGetErrorString(e));
+  return hip_status(e);
 }
 
 namespace {
-// StepArgs of a single-rank step and their checks against the flow's parameter count np
-enf_status step_args(int64_t D, void* theta, void* acc, const int64_t* runs, int32_t nruns, const int64_t* hb,
-                     int32_t nhb, double eta, double epsilon, double* loss_out, int64_t B, int64_t np, StepArgs& a) {
+// The StepArgs of an update normalised by the batch size B, checked against the flow's parameter count np; who: the
+// entry point the messages name. hb_at_D: each Householder batch column must be one D-entry vector of the parameter
+// layout (the step's reduction re-normalises it where it updates it; enf_whitening_apply takes any placement)
+enf_status step_args(const char* who, bool hb_at_D, int64_t D, void* theta, void* acc, const int64_t* runs,
+                     int32_t nruns, const int64_t* hb, int32_t nhb, double eta, double epsilon, double* loss_out,
+                     int64_t B, int64_t np, StepArgs& a) {
+  auto fail = [who](enf_status st, const char* what) { return set_error(st, (std::string(who) + what).c_str()); };
   if (nruns < 0 || nruns > kMaxStepRuns || nhb < 0 || nhb > kMaxStepHB)
-    return set_error(ENF_ERR_UNSUPPORTED, "enf_whitening_step: too many parameter runs or Householder batches");
+    return fail(ENF_ERR_UNSUPPORTED, ": too many parameter runs or Householder batches");
   std::memset(&a, 0, sizeof a);
   a.theta = theta;
   a.acc = acc;
@@ -1509,22 +1391,36 @@ enf_status step_args(int64_t D, void* theta, void* acc, const int64_t* runs, int
     a.runs[i][0] = runs[2 * i];
     a.runs[i][1] = runs[2 * i + 1];
     if (a.runs[i][0] < 0 || a.runs[i][1] < a.runs[i][0] || a.runs[i][1] > np)
-      return set_error(ENF_ERR_INVALID, "enf_whitening_step: parameter run outside theta");
+      return fail(ENF_ERR_INVALID, ": parameter run outside theta");
   }
   for (int i = 0; i < nhb; ++i) {
     for (int q = 0; q < 3; ++q) a.hb[i][q] = hb[3 * i + q];
     if (a.hb[i][0] < 0 || a.hb[i][1] < 0 || a.hb[i][2] < D ||
         (a.hb[i][1] > 0 && a.hb[i][0] + (a.hb[i][1] - 1) * a.hb[i][2] + D > np))
-      return set_error(ENF_ERR_INVALID, "enf_whitening_step: Householder batch outside theta");
-    // (each column is one D-entry vector of the parameter layout: the reduction re-normalises it where it updates it)
-    if (a.hb[i][0] % D != 0 || a.hb[i][2] % D != 0)
-      return set_error(ENF_ERR_INVALID, "enf_whitening_step: Householder batch columns must start at multiples of D");
+      return fail(ENF_ERR_INVALID, ": Householder batch outside theta");
+    if (hb_at_D && (a.hb[i][0] % D != 0 || a.hb[i][2] % D != 0))
+      return fail(ENF_ERR_INVALID, ": Householder batch columns must start at multiples of D");
   }
   return ENF_OK;
 }
+}  // namespace
 
+enf_status whitening_apply(bool f64, int64_t D, int64_t nparams, const void* g, int64_t B, void* theta, void* acc,
+                           const int64_t* runs, int32_t nruns, const int64_t* hb, int32_t nhb, double eta,
+                           double epsilon, double* loss_out, hipStream_t st) {
+  StepArgs a;
+  enf_status s = step_args("enf_whitening_apply", false, D, theta, acc, runs, nruns, hb, nhb, eta, epsilon, loss_out, B,
+                           nparams, a);
+  if (s != ENF_OK) return s;
+  if (f64) hipLaunchKernelGGL((whitening_apply_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)g, a);
+  else hipLaunchKernelGGL((whitening_apply_kernel<float>), dim3(1), dim3(256), 0, st, (const float*)g, a);
+  return hip_status(hipGetLastError());
+}
+
+namespace {
 // the largest gradient-row payload the data-parallel step hands to the collective instead of reducing it first
 constexpr size_t kRowsCollectiveMax = 64 << 10;
+}  // namespace
 
 // B: the global batch size the update normalises by (N on one rank); ar: the cross-rank sum between the gradient
 // and the update (enf_whitening_step_dp), or none; nranks: the ranks of that sum.
@@ -1537,7 +1433,8 @@ enf_status whitening_step_single(bool f64, int64_t D, int64_t N, const void* X, 
   enf_status s = make_plan(f64, D, N > 0 ? N : 1, layers, nlayers, P);
   if (s != ENF_OK) return s;
   StepArgs a;
-  s = step_args(D, theta, acc, runs, nruns, hb, nhb, eta, epsilon, loss_out, B, P.ga.nparams, a);
+  s = step_args("enf_whitening_step", true, D, theta, acc, runs, nruns, hb, nhb, eta, epsilon, loss_out, B,
+                P.ga.nparams, a);
   if (s != ENF_OK) return s;
   const size_t n1 = 1 + (size_t)P.ga.nparams;
   // Data-parallel step of the fused (J o H)^n fp32 kernel over a share of the minibatch (round 6, VERDICT r05 item
@@ -1563,7 +1460,7 @@ enf_status whitening_step_single(bool f64, int64_t D, int64_t N, const void* X, 
     if (N > 0) {
       int nb = 0;
       e = launch_hj_grad(D, N, X, layers, nlayers, P.ga.nparams, rows, rows + (size_t)R * n1, &nb, st, Nplan, true);
-      if (e != hipSuccess) return set_error(ENF_ERR_HIP, hipGetErrorString(e));
+      if (e != hipSuccess) return hip_status(e);
       if (nb != R) return set_error(ENF_ERR_HIP, "enf_whitening_step_dp: unexpected gradient grid");
     } else if (hipMemsetAsync(rows, 0, (size_t)R * n1 * sizeof(double), st) != hipSuccess) {
       return set_error(ENF_ERR_HIP, "hipMemsetAsync");
@@ -1575,7 +1472,7 @@ enf_status whitening_step_single(bool f64, int64_t D, int64_t N, const void* X, 
     P.ra.ctot = nullptr;
     P.ra.tot = rows + (size_t)R * n1;
     e = launch_reduce<MODE_STEP>(f64, P.ra, a, st);
-    return e == hipSuccess ? ENF_OK : set_error(ENF_ERR_HIP, hipGetErrorString(e));
+    return hip_status(e);
   }
   // one rank, a batch of one block, not the fused (J o H)^n kernel: gradient and update in ONE launch (round 5)
   static const int small_ok = ENF_KNOB("ENF_STEP_SMALL", 1);
@@ -1584,8 +1481,8 @@ enf_status whitening_step_single(bool f64, int64_t D, int64_t N, const void* X, 
     P.ga.X = X;
     P.ga.ldx = ldx;
     P.ga.partial = nullptr;
-    hipError_t e = f64 ? launch_step_small<double>(P, a, st) : launch_step_small<float>(P, a, st);
-    return e == hipSuccess ? ENF_OK : set_error(ENF_ERR_HIP, hipGetErrorString(e));
+    hipError_t e = f64 ? launch_small<double>(P, a, st) : launch_small<float>(P, a, st);
+    return hip_status(e);
   }
   if (N > 0) {
     s = grad_parts(f64, D, N, X, ldx, layers, nlayers, workspace, workspace_bytes, st, P);
@@ -1600,7 +1497,7 @@ enf_status whitening_step_single(bool f64, int64_t D, int64_t N, const void* X, 
   if (ar || N <= 0) {
     if (N > 0) {  // this rank's totals (MODE_SUM), the all-reduce, then the update reading the one summed row
       e = launch_reduce<MODE_SUM>(f64, P.ra, a, st);
-      if (e != hipSuccess) return set_error(ENF_ERR_HIP, hipGetErrorString(e));
+      if (e != hipSuccess) return hip_status(e);
     }
     if (ar) {
       s = ar(ar_ctx, P.ra.tot, (int64_t)n1, true, st);
@@ -1611,284 +1508,7 @@ enf_status whitening_step_single(bool f64, int64_t D, int64_t N, const void* X, 
     P.ra.ctot = nullptr;
   }
   e = launch_reduce<MODE_STEP>(f64, P.ra, a, st);
-  return e == hipSuccess ? ENF_OK : set_error(ENF_ERR_HIP, hipGetErrorString(e));
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------------------------
-// Chunked gradient / VJP (round 4, VERDICT r03 missing item 1): a flow beyond one gradient launch's bounds
-// (more than 16 layers or 32 steps, or parameter accumulators and activations that do not fit the LDS, as
-// at large D) runs as consecutive chunks of layers (a chained HouseholderTrafo may be split between its
-// columns), each within the bounds. The forward pass keeps each chunk's input (a checkpoint, D x N) --
-// the reference's pullback recomputes layer inputs instead (householder_trafo.jl:91-101); a checkpoint per
-// chunk is exact and costs one D x N buffer each --, the backward pass runs the chunks' VJP kernels in
-// reverse, each from its checkpoint, the cotangent of the chunk's output and the ladj cotangent, writing the
-// cotangent of its input in place and ACCUMULATING its parameter VJP at the chunk's offset of the flow's
-// gradient layout (a chunk's entries are a contiguous range of it: layers in order, a chained
-// Householder's columns in order). The loss is the device reduction of enf_flow_negll over the last chunk's
-// output and the ladj accumulated over the chunks.
-namespace {
-
-struct GradChunk {
-  std::vector<enf_layer> layers;
-  int64_t goff = 0;     // first gradient entry of the chunk in the flow's layout
-  int64_t nparams = 0;  // its gradient entries
-};
-
-bool fits_one_launch(bool f64, int64_t D, int64_t N, const enf_layer* layers, int32_t nlayers) {
-  Plan P;
-  return make_plan(f64, D, N > 0 ? N : 1, layers, nlayers, P) == ENF_OK && P.lds <= kGradLdsMax;
-}
-
-// Greedy chunks: units (one layer, or one column of a chained Householder) are appended while the chunk
-// fits one launch.
-enf_status plan_chunks(bool f64, int64_t D, int64_t N, const enf_layer* layers, int32_t nlayers,
-                       std::vector<GradChunk>& out) {
-  out.clear();
-  const size_t esz = f64 ? 8 : 4;
-  GradChunk cur;
-  int64_t goff = 0;
-  auto unit_layer = [&](int32_t l, int32_t c) {
-    enf_layer u = layers[l];
-    if (u.op == ENF_OP_HOUSEHOLDER) {
-      u.k = 1;
-      u.p[0] = (const char*)layers[l].p[0] + (size_t)c * (size_t)D * esz;
-    }
-    return u;
-  };
-  for (int32_t l = 0; l < nlayers; ++l) {
-    const int32_t ncol = layers[l].op == ENF_OP_HOUSEHOLDER ? layers[l].k : 1;
-    const int64_t per = layers[l].op == ENF_OP_HOUSEHOLDER ? D : D * grad_nparams(layers[l].op);
-    for (int32_t c = 0; c < ncol; ++c) {
-      const enf_layer u = unit_layer(l, c);
-      std::vector<enf_layer> trial = cur.layers;
-      // the next column of the same chained Householder extends the chunk's last sub-layer
-      const bool merge = c > 0 && !trial.empty() && trial.back().op == ENF_OP_HOUSEHOLDER &&
-                         (const char*)trial.back().p[0] + (size_t)trial.back().k * (size_t)D * esz == (const char*)u.p[0];
-      if (merge) trial.back().k += 1;
-      else trial.push_back(u);
-      if (fits_one_launch(f64, D, N, trial.data(), (int32_t)trial.size())) {
-        cur.layers.swap(trial);
-        cur.nparams += per;
-      } else {
-        if (cur.layers.empty())
-          return set_error(ENF_ERR_UNSUPPORTED, "enf_flow_negll_grad: one transform exceeds the gradient kernel's bounds");
-        out.push_back(cur);
-        cur = GradChunk();
-        cur.goff = goff;
-        cur.layers.push_back(u);
-        cur.nparams = per;
-        if (!fits_one_launch(f64, D, N, cur.layers.data(), 1))
-          return set_error(ENF_ERR_UNSUPPORTED, "enf_flow_negll_grad: one transform exceeds the gradient kernel's bounds");
-      }
-      goff += per;
-    }
-  }
-  if (!cur.layers.empty()) out.push_back(cur);
-  set_error(ENF_OK, "");
-  return ENF_OK;
-}
-
-size_t al256g(size_t b) { return (b + 255) / 256 * 256; }
-
-struct ChunkWs {
-  size_t ck = 0, y = 0, l = 0, m1 = 0, part = 0, g = 0, vws = 0, total = 0;  // byte offsets / sizes
-  size_t vws_bytes = 0;
-};
-
-// Workspace layout of the chunked calls: [checkpoints (m - 1) x D x N][Y or the cotangent buffer: D x N]
-// [ladj: N][-1 vector: N][loss partials][whitening: g (1 + nparams)][the chunks' VJP workspace (largest)]
-enf_status chunk_ws(bool f64, int64_t D, int64_t N, const std::vector<GradChunk>& ch, int64_t nparams, ChunkWs& w) {
-  const size_t e = f64 ? 8 : 4, DN = (size_t)D * (size_t)(N > 0 ? N : 1), Nn = (size_t)(N > 0 ? N : 1);
-  size_t off = 0;
-  w.ck = off;
-  off += al256g((ch.size() - 1) * DN * e);
-  w.y = off;
-  off += al256g(DN * e);
-  w.l = off;
-  off += al256g(Nn * e);
-  w.m1 = off;
-  off += al256g(Nn * e);
-  w.part = off;
-  off += al256g(1025 * sizeof(double));
-  w.g = off;
-  off += al256g((size_t)(1 + nparams) * e);
-  w.vws = off;
-  w.vws_bytes = 0;
-  for (const GradChunk& c : ch) {
-    size_t b = 0;
-    enf_status s = single_workspace(f64, D, N > 0 ? N : 1, c.layers.data(), (int32_t)c.layers.size(), &b);
-    if (s != ENF_OK) return s;
-    w.vws_bytes = std::max(w.vws_bytes, b);
-  }
-  w.total = off + al256g(w.vws_bytes);
-  return ENF_OK;
-}
-
-template <typename T>
-__global__ void fill_kernel(T* __restrict__ p, int64_t n, T v) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
-}
-
-enf_status fill(bool f64, void* p, int64_t n, double v, hipStream_t st) {
-  const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 1024);
-  if (f64) hipLaunchKernelGGL((fill_kernel<double>), dim3(nb > 0 ? nb : 1), dim3(256), 0, st, (double*)p, n, v);
-  else hipLaunchKernelGGL((fill_kernel<float>), dim3(nb > 0 ? nb : 1), dim3(256), 0, st, (float*)p, n, (float)v);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ENF_OK : set_error(ENF_ERR_HIP, hipGetErrorString(e));
-}
-
-int64_t total_params(int64_t D, const enf_layer* layers, int32_t nlayers) {
-  int64_t n = 0;
-  for (int32_t l = 0; l < nlayers; ++l) n += D * (layers[l].op == ENF_OP_HOUSEHOLDER ? layers[l].k : grad_nparams(layers[l].op));
-  return n;
-}
-
-// forward over the chunks: checkpoints of chunks 1 .. m-1's inputs; with Yout, the last chunk's output and the
-// ladj summed over all chunks (L)
-enf_status chunk_forward(bool f64, int64_t D, int64_t N, const void* X, int64_t ldx, const std::vector<GradChunk>& ch,
-                         char* ws, const ChunkWs& w, bool want_y, hipStream_t st) {
-  const size_t e = f64 ? 8 : 4, DN = (size_t)D * (size_t)N;
-  const void* cur = X;
-  int64_t ld = ldx;
-  const size_t m = ch.size();
-  for (size_t c = 0; c + (want_y ? 0 : 1) < m; ++c) {
-    void* dst = c + 1 < m ? (void*)(ws + w.ck + c * DN * e) : (void*)(ws + w.y);
-    enf_status s = enf_flow_apply(f64 ? ENF_F64 : ENF_F32, D, N, cur, ld, dst, D, want_y ? ws + w.l : nullptr,
-                                  c > 0 ? 1 : 0, ch[c].layers.data(), (int32_t)ch[c].layers.size(), st);
-    if (s != ENF_OK) return s;
-    cur = dst;
-    ld = D;
-  }
-  return ENF_OK;
-}
-
-// backward over the chunks from the cotangent in `cot` (D x N, ld D, overwritten): the last chunk reads dY
-// (ld lddy; may be cot), the first writes dX (ld lddx; may be cot); parameter VJPs into dparams + offsets
-enf_status chunk_backward(bool f64, int64_t D, int64_t N, const void* X, int64_t ldx, const void* dY, int64_t lddy,
-                          const void* dladj, const std::vector<GradChunk>& ch, void* dX, int64_t lddx, char* dparams,
-                          char* ws, const ChunkWs& w, hipStream_t st) {
-  const size_t e = f64 ? 8 : 4, DN = (size_t)D * (size_t)N;
-  void* cot = ws + w.y;
-  for (size_t c = ch.size(); c-- > 0;) {
-    const void* in = c == 0 ? X : (const void*)(ws + w.ck + (c - 1) * DN * e);
-    const int64_t ldin = c == 0 ? ldx : D;
-    const void* gy = c + 1 == ch.size() ? dY : cot;
-    const int64_t ldgy = c + 1 == ch.size() ? lddy : D;
-    void* gx = c == 0 ? dX : cot;
-    const int64_t ldgx = c == 0 ? lddx : D;
-    enf_status s = flow_vjp_single(f64, D, N, in, ldin, gy, ldgy, dladj, ch[c].layers.data(), (int32_t)ch[c].layers.size(),
-                                   gx, ldgx, dparams ? dparams + (size_t)ch[c].goff * e : nullptr, ws + w.vws,
-                                   w.vws_bytes, st);
-    if (s != ENF_OK) return s;
-  }
-  return ENF_OK;
-}
-
-// ENF_NEGLL_ZYGOTE on the chunked path: out[0] += N sum log|a| over the flow's ScaleShiftTrafos (one wave; the
-// one-launch path adds the same inside the gradient kernel, scaleshift_ladj_lane)
-constexpr int kZygoteMaxSS = 64;
-struct ZygoteSS {
-  const void* p[kZygoteMaxSS];
-  int32_t n[kZygoteMaxSS];
-  int32_t cnt;
-};
-template <typename T>
-__global__ __launch_bounds__(64) void zygote_loss_kernel(T* out, ZygoteSS z, int64_t N) {
-  double s = 0.0;
-  for (int i = 0; i < z.cnt; ++i)
-    for (int d = threadIdx.x; d < z.n[i]; d += 64) s += log(fabs((double)((const T*)z.p[i])[d]));
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-  if (threadIdx.x == 0) out[0] += (T)((double)N * s);
-}
-enf_status zygote_loss_chunked(bool f64, int64_t D, int64_t N, const std::vector<GradChunk>& ch, void* out,
-                               hipStream_t st) {
-  ZygoteSS z;
-  std::memset(&z, 0, sizeof z);
-  for (const GradChunk& c : ch)
-    for (const enf_layer& l : c.layers) {
-      if (l.op != OP_SCALESHIFT) continue;
-      if (z.cnt == kZygoteMaxSS) return set_error(ENF_ERR_UNSUPPORTED, "ENF_NEGLL_ZYGOTE: more than 64 ScaleShiftTrafos");
-      z.p[z.cnt] = l.p[0];
-      z.n[z.cnt++] = l.k == 1 ? 1 : (int32_t)D;
-    }
-  if (z.cnt == 0) return ENF_OK;
-  if (f64) hipLaunchKernelGGL(zygote_loss_kernel<double>, dim3(1), dim3(64), 0, st, (double*)out, z, N);
-  else hipLaunchKernelGGL(zygote_loss_kernel<float>, dim3(1), dim3(64), 0, st, (float*)out, z, N);
-  const hipError_t h = hipGetLastError();
-  return h == hipSuccess ? ENF_OK : set_error(ENF_ERR_HIP, hipGetErrorString(h));
-}
-
-// the whole negll + gradient through the chunks into out (1 + nparams of T, accumulated)
-enf_status negll_grad_chunked(bool f64, int64_t D, int64_t N, const void* X, int64_t ldx,
-                              const std::vector<GradChunk>& ch, void* out, char* ws, const ChunkWs& w, hipStream_t st) {
-  const size_t e = f64 ? 8 : 4;
-  enf_status s = chunk_forward(f64, D, N, X, ldx, ch, ws, w, true, st);
-  if (s != ENF_OK) return s;
-  double* part = (double*)(ws + w.part);
-  s = negll_reduce(f64, D, N, ws + w.y, ws + w.l, part, part + 1024, true, st);
-  if (s == ENF_OK) s = negll_add_total(f64, part + 1024, out, st);
-  if (s == ENF_OK && tl_negll_zygote) s = zygote_loss_chunked(f64, D, N, ch, out, st);
-  if (s == ENF_OK) s = fill(f64, ws + w.m1, N, -1.0, st);  // d(loss)/d(ladj) = -1; d(loss)/dY = Y (in place)
-  if (s != ENF_OK) return s;
-  return chunk_backward(f64, D, N, X, ldx, ws + w.y, D, ws + w.m1, ch, ws + w.y, D, (char*)out + e, ws, w, st);
-}
-
-}  // namespace
-
-enf_status negll_grad_workspace(bool f64, int64_t D, int64_t N, const enf_layer* layers, int32_t nlayers,
-                                size_t* bytes) {
-  if (fits_one_launch(f64, D, N, layers, nlayers)) return single_workspace(f64, D, N > 0 ? N : 1, layers, nlayers, bytes);
-  std::vector<GradChunk> ch;
-  enf_status s = plan_chunks(f64, D, N, layers, nlayers, ch);
-  if (s != ENF_OK) return s;
-  ChunkWs w;
-  s = chunk_ws(f64, D, N, ch, total_params(D, layers, nlayers), w);
-  if (s != ENF_OK) return s;
-  *bytes = w.total;
-  return ENF_OK;
-}
-
-namespace {
-enf_status chunked_setup(bool f64, int64_t D, int64_t N, const enf_layer* layers, int32_t nlayers, void* workspace,
-                         size_t workspace_bytes, std::vector<GradChunk>& ch, ChunkWs& w, const char* who) {
-  enf_status s = plan_chunks(f64, D, N, layers, nlayers, ch);
-  if (s != ENF_OK) return s;
-  s = chunk_ws(f64, D, N, ch, total_params(D, layers, nlayers), w);
-  if (s != ENF_OK) return s;
-  if (!workspace || workspace_bytes < w.total)
-    return set_error(ENF_ERR_INVALID, (std::string(who) + ": workspace too small (chunked flow: " +
-                                       std::to_string(w.total) + " bytes, enf_flow_negll_grad_workspace)").c_str());
-  return ENF_OK;
-}
-}  // namespace
-
-enf_status negll_grad(bool f64, int64_t D, int64_t N, const void* X, int64_t ldx, const enf_layer* layers,
-                      int32_t nlayers, void* out, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (fits_one_launch(f64, D, N, layers, nlayers))
-    return negll_grad_single(f64, D, N, X, ldx, layers, nlayers, out, workspace, workspace_bytes, st);
-  std::vector<GradChunk> ch;
-  ChunkWs w;
-  enf_status s = chunked_setup(f64, D, N, layers, nlayers, workspace, workspace_bytes, ch, w, "enf_flow_negll_grad");
-  if (s != ENF_OK) return s;
-  return negll_grad_chunked(f64, D, N, X, ldx, ch, out, (char*)workspace, w, st);
-}
-
-enf_status flow_vjp(bool f64, int64_t D, int64_t N, const void* X, int64_t ldx, const void* dY, int64_t lddy,
-                    const void* dladj, const enf_layer* layers, int32_t nlayers, void* dX, int64_t lddx, void* dparams,
-                    void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (fits_one_launch(f64, D, N, layers, nlayers))
-    return flow_vjp_single(f64, D, N, X, ldx, dY, lddy, dladj, layers, nlayers, dX, lddx, dparams, workspace,
-                           workspace_bytes, st);
-  std::vector<GradChunk> ch;
-  ChunkWs w;
-  enf_status s = chunked_setup(f64, D, N, layers, nlayers, workspace, workspace_bytes, ch, w, "enf_flow_vjp");
-  if (s != ENF_OK) return s;
-  char* ws = (char*)workspace;
-  s = chunk_forward(f64, D, N, X, ldx, ch, ws, w, false, st);
-  if (s != ENF_OK) return s;
-  return chunk_backward(f64, D, N, X, ldx, dY, lddy, dladj, ch, dX, lddx, (char*)dparams, ws, w, st);
+  return hip_status(e);
 }
 
 enf_status whitening_step(bool f64, int64_t D, int64_t N, const void* X, int64_t ldx, const enf_layer* layers,
@@ -1897,34 +1517,6 @@ enf_status whitening_step(bool f64, int64_t D, int64_t N, const void* X, int64_t
                           void* workspace, size_t workspace_bytes, hipStream_t st) {
   return whitening_step_dp(f64, D, N, X, ldx, layers, nlayers, theta, acc, runs, nruns, hb, nhb, eta, epsilon, N,
                            loss_out, nullptr, nullptr, workspace, workspace_bytes, st, 1);
-}
-
-enf_status whitening_step_dp(bool f64, int64_t D, int64_t N, const void* X, int64_t ldx, const enf_layer* layers,
-                             int32_t nlayers, void* theta, void* acc, const int64_t* runs, int32_t nruns,
-                             const int64_t* hb, int32_t nhb, double eta, double epsilon, int64_t B, double* loss_out,
-                             AllreduceFn ar, void* ar_ctx, void* workspace, size_t workspace_bytes, hipStream_t st,
-                             int nranks) {
-  if (fits_one_launch(f64, D, N, layers, nlayers))
-    return whitening_step_single(f64, D, N, X, ldx, layers, nlayers, theta, acc, runs, nruns, hb, nhb, eta, epsilon,
-                                 loss_out, workspace, workspace_bytes, st, B, ar, ar_ctx, nranks);
-  std::vector<GradChunk> ch;
-  ChunkWs w;
-  enf_status s = chunked_setup(f64, D, N, layers, nlayers, workspace, workspace_bytes, ch, w, "enf_whitening_step");
-  if (s != ENF_OK) return s;
-  // the gradient sums into g (zeroed), then the update half of the step (enf_whitening_apply's kernel, B = N)
-  char* ws = (char*)workspace;
-  const int64_t np = total_params(D, layers, nlayers);
-  if (hipMemsetAsync(ws + w.g, 0, (size_t)(1 + np) * (f64 ? 8 : 4), st) != hipSuccess)
-    return set_error(ENF_ERR_HIP, "hipMemsetAsync");
-  if (N > 0) {
-    s = negll_grad_chunked(f64, D, N, X, ldx, ch, ws + w.g, ws, w, st);
-    if (s != ENF_OK) return s;
-  }
-  if (ar) {
-    s = ar(ar_ctx, ws + w.g, 1 + np, f64, st);
-    if (s != ENF_OK) return s;
-  }
-  return whitening_apply(f64, D, np, ws + w.g, B, theta, acc, runs, nruns, hb, nhb, eta, epsilon, loss_out, st);
 }
 
 // The single-rank steps of one epoch (enf_whitening_epoch): the minibatches [b0, b0 + bs) of the N columns in order,
@@ -1955,14 +1547,15 @@ enf_status whitening_epoch(bool f64, int64_t D, int64_t N, const void* X, int64_
         if (Q.blocks == 1 && Q.vl == P.vl && Q.nw == P.nw) ncols = N;
       }
       StepArgs a;
-      s = step_args(D, theta, acc, runs, nruns, hb, nhb, eta, epsilon, loss_out, bs, P.ga.nparams, a);
+      s = step_args("enf_whitening_step", true, D, theta, acc, runs, nruns, hb, nhb, eta, epsilon, loss_out, bs,
+                    P.ga.nparams, a);
       if (s != ENF_OK) return s;
       P.ga.X = X;
       P.ga.ldx = ldx;
       P.ga.partial = nullptr;
       if (ncols > 0) {
-        hipError_t e = f64 ? launch_epoch_small<double>(P, a, ncols, bs, st) : launch_epoch_small<float>(P, a, ncols, bs, st);
-        if (e != hipSuccess) return set_error(ENF_ERR_HIP, hipGetErrorString(e));
+        hipError_t e = f64 ? launch_small<double>(P, a, st, ncols, bs) : launch_small<float>(P, a, st, ncols, bs);
+        if (e != hipSuccess) return hip_status(e);
       }
       done = (ncols + bs - 1) / bs;
     }

@@ -87,17 +87,6 @@ __device__ __forceinline__ float prod_rows(const float (&q)[V]) {
   else return q[0];
 }
 
-// cross-slot sum: lanes with equal lane % G hold the same rows
-template <int G>
-__device__ __forceinline__ float slot_sum(float v) {
-  // strides G, 2G, ... < 64 in that order, as `v += __shfl_xor(v, m)`, without LDS round trips (enf_train.h)
-  static_assert(G >= 8, "D >= 32, at most 4 rows per lane");
-  if constexpr (G == 8) v += dpp_mov<0x128>(v);  // row_ror:8 = lane ^ 8
-  if constexpr (G <= 16) v = add_xor_swap<16>(v);
-  if constexpr (G <= 32) v = add_xor_swap<32>(v);
-  return v;
-}
-
 // the records of the lane's rows r0 = V grp .. r0 + V - 1 (layout [pair][4-row group][param][4]); parameter q at +4q
 template <int D, int V>
 __device__ __forceinline__ const float* rec_lane(const float* __restrict__ rec, int p, int grp) {
@@ -233,8 +222,8 @@ __device__ __forceinline__ void grad_tile(const HJGradArgs& a, int64_t col0, int
     float* ap = acc + (size_t)p * 5 * D + V * grp;
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-      const float sV = slot_sum<G>(aV[e]), sG = slot_sum<G>(aG[e]), sD = slot_sum<G>(aD[e]);
-      const float sX = slot_sum<G>(aX[e]), sL = slot_sum<G>(aL[e]);
+      const float sV = class_sum<G>(aV[e]), sG = class_sum<G>(aG[e]), sD = class_sum<G>(aD[e]);
+      const float sX = class_sum<G>(aX[e]), sL = class_sum<G>(aL[e]);
       if (lane < G) {
         ap[e] += sV;
         ap[D + e] += sG;
@@ -335,7 +324,7 @@ __device__ __forceinline__ void grad_epilogue(const HJGradArgs& a, double* __res
                                               const float* __restrict__ acc0, size_t wstride, double lossp, int nvalid) {
   const int n = a.n;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  lossp = xor_tree(lossp, 64);  // the 64-lane xor butterfly (enf_train.h)
+  lossp = xor_tree(lossp, 64);  // the 64-lane xor butterfly (enf_xlane.h)
   nvalid = xor_tree(nvalid, 64);
   double* wl = scr + 16;
   if (lane == 0) {
@@ -603,7 +592,7 @@ __global__ __launch_bounds__(64 * W) void hj_grad_reg_kernel(HJGradArgs a) {
     for (int k = 0; k < 5; ++k)
 #pragma unroll
       for (int e = 0; e < V; ++e) {
-        const float sv = slot_sum<G>(acc[p][k][e]);
+        const float sv = class_sum<G>(acc[p][k][e]);
         if (lane < G) wacc[(p * 5 + k) * D + V * lane + e] = sv;
       }
   __syncthreads();
@@ -780,13 +769,13 @@ hipError_t launch_hj_grad(int64_t D, int64_t N, const void* X, const enf_layer* 
     const enf_layer& J = layers[2 * p + 1];
     a.v[p] = (const float*)H.p[0];
     a.goffH[p] = off;
-    off += (int32_t)D;
+    off += (int32_t)D * layer_param_vectors(H.op, H.k);
     a.g[p] = (const float*)J.p[0];
     a.d[p] = (const float*)J.p[1];
     a.xi[p] = (const float*)J.p[2];
     a.lam[p] = (const float*)J.p[3];
     a.goffJ[p] = off;
-    off += 4 * (int32_t)D;
+    off += (int32_t)D * layer_param_vectors(J.op, J.k);
   }
   if (off != nparams) return hipErrorInvalidValue;
   const int64_t Np = Nplan > 0 ? Nplan : N;

@@ -195,11 +195,7 @@ __device__ __forceinline__ void normalize_lds(T* __restrict__ v, int D, int lane
     if (lane < D) v[lane] = r;
     return;
   }
-  double ss = 0.0;
-  for (int d = lane; d < D; d += 64) ss += (double)v[d] * (double)v[d];
-  ss = lane_sum(ss, D);
-  const T inv = (T)(1.0 / sqrt(ss));
-  for (int d = lane; d < D; d += 64) v[d] *= inv;
+  normalize_column<T>(v, D, lane);
 }
 
 // The update of a whole flow by ONE block (the single-block fused step, round 5): tot (LDS: 1 + np doubles, the

@@ -87,6 +87,20 @@ __host__ __device__ constexpr int record_width(int op) {
 }
 inline int record_width_host(int op) { return record_width(op); }
 
+// Parameter vectors (D values each) of a layer in the gradient / theta layout (include/enf.h enf_flow_param_count):
+// a chained HouseholderTrafo has its k columns, an elementwise map a fixed count. op must be a public op.
+__host__ __device__ constexpr int layer_param_vectors(int op, int k) {
+  return op == OP_HOUSEHOLDER ? k : op == OP_SCALESHIFT ? 2 : (op == OP_JOHNSON || op == OP_JOHNSON_INV) ? 4 : 3;
+}
+
+// n rounded up to a power of two (n >= 1), as R
+template <typename R = int64_t>
+__host__ __device__ constexpr R next_pow2(int64_t n) {
+  R p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+
 // The fragment (fast) kernel handles power-of-two D up to 256 (fp32) / 128 (fp64: at most 64 lanes
 // per column), contiguous columns (ld == D) and 16-byte aligned X / Y; everything else runs on the
 // generic kernel.
@@ -104,9 +118,7 @@ inline int64_t frag_pad_dim(int64_t D, int64_t ldx, int64_t ldy, const void* X, 
   const int64_t dmax = elem == 4 ? 256 : 128, v = (int64_t)(16 / elem);
   if (D < v || D > dmax || (D & (D - 1)) == 0 || D % v != 0 || ldx != D || ldy != D) return 0;
   if (((((uintptr_t)X) | ((uintptr_t)Y)) & 15) != 0) return 0;
-  int64_t p = 1;
-  while (p < D) p <<= 1;
-  return p;
+  return next_pow2(D);
 }
 
 // Values of T in one step's LDS record: W * max(D, RV) (RV = 16/elem on the fragment path, else 1),

@@ -116,6 +116,33 @@ def test_param_count(enf):
     assert n.value == 32 * 3 + 32 * 4 + 32 * 2
 
 
+def test_whitening_apply_argument_checks(enf):
+    """enf_whitening_apply (f64, D = 2, nparams = 8, B = 4, host buffers) rejects parameter runs and Householder
+    batches outside theta, and too many of either, with its own name in the message and before any device call."""
+    L = enf._lib.lib()
+    g, theta, acc = np.zeros(9), np.zeros(8), np.zeros(8)
+    loss = ctypes.c_double()
+
+    def apply(runs, hbs):
+        r = np.ascontiguousarray(np.array(runs, dtype=np.int64).reshape(-1))
+        h = np.ascontiguousarray(np.array(hbs, dtype=np.int64).reshape(-1))
+        st = L.enf_whitening_apply(enf._lib.ENF_F64, 2, 8, g.ctypes.data, 4, theta.ctypes.data, acc.ctypes.data,
+                                   r.ctypes.data if len(runs) else None, len(runs),
+                                   h.ctypes.data if len(hbs) else None, len(hbs), 0.1, 1e-8,
+                                   ctypes.addressof(loss), None)
+        return st, L.enf_last_error().decode()
+
+    for run in ([0, 9], [4, 2], [-1, 2]):
+        assert apply([run], []) == (enf._lib.ENF_ERR_INVALID, "enf_whitening_apply: parameter run outside theta"), run
+    for hb in ((0, -1, 2), (0, 1, 1), (6, 2, 2)):
+        assert apply([], [hb]) == (enf._lib.ENF_ERR_INVALID,
+                                   "enf_whitening_apply: Householder batch outside theta"), hb
+    many = "enf_whitening_apply: too many parameter runs or Householder batches"
+    assert apply([[0, 1]] * 65, []) == (enf._lib.ENF_ERR_UNSUPPORTED, many)
+    assert apply([], [(0, 1, 2)] * 17) == (enf._lib.ENF_ERR_UNSUPPORTED, many)
+    assert (enf._lib.ENF_ERR_INVALID, enf._lib.ENF_ERR_UNSUPPORTED) == (1, 3)
+
+
 def test_comm_validation(enf):
     L = enf._lib.lib()
     comm = ctypes.c_void_p()

@@ -8,9 +8,10 @@
   chunked path; the offset is checked per step against the oracle's.
 * Minibatch sizes round half to even (Julia's round(Int, N/nbatches), src/optimize_whitening.jl:31): the oracle
   used to round half away from zero; a tie size now matches the device.
-* The cross-lane sums of enf_train.h (the xor tree and the permlane swaps written as inline asm with a hand-placed
-  hazard pad) equal the __shfl_xor butterfly bit for bit at every group size (the round-5
-  run-27 miscompile of the swap builtin gave wrong gradient sums).
+* The cross-lane sums of enf_xlane.h (the xor tree, the group sums and the permlane swaps written as inline asm with
+  a hand-placed hazard pad) equal the __shfl_xor butterfly bit for bit at every group size, the class sums the exact
+  sum (the round-5 run-27 miscompile of the swap builtin gave wrong gradient sums).
+* A Householder batch that does not start at a multiple of D is rejected by enf_whitening_step alone.
 * The gradient workspace of enf_flow_negll_grad_workspace(batchsize) suffices for a ragged last minibatch below
   the fused kernel's shape switch.
 * Elementwise accuracy: the fraction of output elements within rtol * |y| of the
@@ -188,6 +189,44 @@ def test_epoch_large_batch_ragged_tail_workspace(enf, gpu):
     assert torch.equal(sa.theta, sb.theta) and torch.equal(sa.acc, sb.acc)
 
 
+def test_householder_batch_placement_is_checked_by_the_step_only(enf, gpu):
+    """A Householder batch whose columns do not start at multiples of D (D = 2, one ScaleShiftTrafo, offset 1):
+    enf_whitening_step rejects it before launching anything -- its reduction re-normalises a column where it updates
+    it, as one D-entry vector of the parameter layout --, enf_whitening_apply, which normalises after the update,
+    accepts it."""
+    import torch
+
+    from euclidiannormalizingflows_jl_amd import _lib
+    from euclidiannormalizingflows_jl_amd.train import FlowState, _workspace
+
+    rng = np.random.default_rng(6350)
+    D, N = 2, 4
+    f = make_flow(enf, [(0, rand_params(rng, 0, D, np.float64))])
+    X = colmajor_cuda(rng.standard_normal((D, N)))
+    opt = enf.ADAGrad()
+    st = FlowState(f, D, torch.float64, X.device, opt)
+    assert st.nparams == 4
+    ws = _workspace(st, N)
+    L = _lib.lib()
+    hbs = np.array([1, 1, 2], dtype=np.int64)  # offset, k, ldv
+    loss = torch.zeros(1, dtype=torch.float64, device=X.device)
+    th0, ac0 = st.theta.clone(), st.acc.clone()
+    rc = L.enf_whitening_step(_lib.ENF_F64, D, N, X.data_ptr(), X.stride(1), st.layers(), len(st.trafos),
+                              st.theta.data_ptr(), st.acc.data_ptr(), None, 0, hbs.ctypes.data, 1, opt.eta,
+                              opt.epsilon, loss.data_ptr(), ws.data_ptr(), ws.numel() * 8, None)
+    assert rc == _lib.ENF_ERR_INVALID
+    assert L.enf_last_error().decode() == "enf_whitening_step: Householder batch columns must start at multiples of D"
+    torch.cuda.synchronize()
+    assert torch.equal(st.theta, th0) and torch.equal(st.acc, ac0) and float(loss[0]) == 0.0
+    g = torch.zeros(1 + st.nparams, dtype=torch.float64, device=X.device)
+    rc = L.enf_whitening_apply(_lib.ENF_F64, D, st.nparams, g.data_ptr(), N, st.theta.data_ptr(), st.acc.data_ptr(),
+                               None, 0, hbs.ctypes.data, 1, opt.eta, opt.epsilon, loss.data_ptr(), None)
+    assert rc == _lib.ENF_OK, L.enf_last_error().decode()
+    torch.cuda.synchronize()
+    th = st.theta.cpu().numpy()
+    assert abs(np.linalg.norm(th[1:3]) - 1.0) < 1e-15 and th[0] == float(th0[0]) and th[3] == float(th0[3])
+
+
 def _xlane_lib():
     path = os.path.join(ROOT, "tests", "xlane", "libenf_xlane.so")
     if not os.path.exists(path):
@@ -196,22 +235,40 @@ def _xlane_lib():
     lib = ctypes.CDLL(path)
     lib.enf_xlane_check.restype = ctypes.c_int
     lib.enf_xlane_check.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.enf_xlane_group_check.restype = ctypes.c_int
+    lib.enf_xlane_group_check.argtypes = lib.enf_xlane_check.argtypes
     return lib
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_cross_lane_primitives(enf, gpu, dtype):
-    """enf_train.h's xor_tree over groups of P = 1 .. 64 lanes, add_xor_swap<16> / <32> (v_permlane16/32_swap as
-    inline asm after an `s_nop 1` hazard pad) and lane_sum equal the __shfl_xor butterfly bit for bit, over inputs
-    whose sums round differently in every association (tests/xlane/xlane.hip, a test-only library)."""
+    """enf_xlane.h's xor_tree over groups of P = 1 .. 64 lanes, add_xor_swap<16> / <32> (v_permlane16/32_swap as
+    inline asm after an `s_nop 1` hazard pad), lane_sum and both flavours of group_sum<G> equal the __shfl_xor
+    butterfly bit for bit, over inputs whose sums round differently in every association; class_sum<G> gives lanes
+    < G the sum over the lanes of their class lane % G, over integer inputs whose sums are exact in any association
+    (its stage order is not the butterfly's for G < 8) (tests/xlane/xlane.hip, a test-only library)."""
     import torch
 
     lib = _xlane_lib()
     rng = np.random.default_rng(6400)
     td = torch.float32 if dtype == np.float32 else torch.float64
+    code, bits = (0, np.uint32) if dtype == np.float32 else (1, np.uint64)
     for trial in range(8):
         vals = (rng.standard_normal(64) * 10.0 ** rng.uniform(-8, 8, 64)).astype(dtype)
         x = torch.from_numpy(vals).cuda()
+        ints = rng.permutation(1000)[:64] + 1  # distinct integers in [1, 1000]: every partial sum is exact
+        xi = torch.from_numpy(ints.astype(dtype)).cuda()
+        for G in (1, 2, 4, 8, 16, 32, 64):
+            out = torch.full((256,), float("nan"), dtype=td, device="cuda")
+            assert lib.enf_xlane_group_check(code, G, x.data_ptr(), out.data_ptr(), None) == 0
+            outi = torch.full((256,), float("nan"), dtype=td, device="cuda")
+            assert lib.enf_xlane_group_check(code, G, xi.data_ptr(), outi.data_ptr(), None) == 0
+            torch.cuda.synchronize()
+            o = out.cpu().numpy().view(bits)
+            assert np.array_equal(o[0:64], o[128:192]), (trial, G, "group_sum, shuffle strides")
+            assert np.array_equal(o[64:128], o[128:192]), (trial, G, "group_sum, swap strides")
+            cls = outi.cpu().numpy()[192:192 + G]
+            assert np.array_equal(cls, ints.reshape(64 // G, G).sum(axis=0).astype(dtype)), (trial, G, "class_sum")
         for P in (1, 2, 4, 8, 16, 32, 64):
             out = torch.full((448,), float("nan"), dtype=td, device="cuda")
             assert lib.enf_xlane_check(0 if dtype == np.float32 else 1, P, x.data_ptr(), out.data_ptr(), None) == 0
